@@ -12,6 +12,11 @@ line.  The lattice is split into N row stripes: by default the SAM
 lattice at any N (strong scaling, 1024 / N rows per GPU, as BASELINE.json's metric is quoted at
 N = 1M); --weak keeps --rows rows per GPU instead.  Ranks exchange ghost rows every few steps
 through ONE RCCL all-to-all (neighbour rows + guard records).  Prints ONE JSON line on rank 0.
+
+A plain run does what the headline needs: set-up, warm-up, the timed steps (and, for the lattice,
+their statistics replay, which counts the solves), --dump-outputs, the line.  --full adds every
+other record: the per-step-outputs replay, kernel and roofline timings, the full-size check, the
+cfg4f / cfg4r regimes, the exchange timing, the end-state digest and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -56,6 +61,36 @@ def progress(msg):
     ws, rank, _ = _dist_env()
     sys.stderr.write(f"bench.py rank {rank}/{ws} (pid {os.getpid()}): {msg}\n")
     sys.stderr.flush()
+
+
+DUMP_BYTES_MAX = 60 * 10 ** 6   # array bytes of one --dump-outputs (the .npy headers keep it under 64 MB)
+
+
+def dump_outputs(args, arrays):
+    """--dump-outputs DIR: the arrays the timed path left after its last timed step (what its
+    caller holds then), one DIR/<name>.npy each: float64 as it is, integer outputs as float32
+    (exact below 2^24).  The inputs are a function of the arguments (--seed), so two builds run
+    with the same arguments are compared output for output.  Outputs over DUMP_BYTES_MAX are cut,
+    all arrays alike, to a fixed seeded sample of their leading index (agents, scenarios)."""
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype != np.float64:
+            if a.size and np.abs(a).max() >= 2 ** 24:
+                raise RuntimeError(f"--dump-outputs: {name} does not fit float32 exactly")
+            a = a.astype(np.float32)
+        host[name] = a
+    n = {a.shape[0] for a in host.values()}
+    if len(n) != 1:
+        raise RuntimeError(f"--dump-outputs: leading sizes differ ({sorted(n)})")
+    n = n.pop()
+    keep = DUMP_BYTES_MAX // sum(a[0].nbytes for a in host.values())
+    idx = None if keep >= n else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a if idx is None else a[idx])
+    progress(f"{args.config}: outputs of the last timed step in {args.dump_outputs} ("
+             + ("whole" if idx is None else f"{keep} of {n} leading indices") + ")")
 
 
 def default_rank_timeout(args):
@@ -401,7 +436,7 @@ def bench_lattice(args, ws, rank, local):
                     S.capture(steps=n)
             else:
                 S.capture()
-        if chunk > 1 and not args.timed_stats and args.barrier == "reference":
+        if args.full and chunk > 1 and not args.timed_stats and args.barrier == "reference":
             # the per-step-outputs variant (history), statistics off
             S.collect_stats = False
             for n in set(plan):
@@ -450,13 +485,16 @@ def bench_lattice(args, ws, rank, local):
 
     # the window cull's degradation counters (workspace header, counted whatever collect_stats says)
     # around the timed steps themselves: egos that walked, guard words read at their spin limit
-    wc = hasattr(S, "window_counters") and S.cull == "window"
+    wc = args.full and hasattr(S, "window_counters") and S.cull == "window"
     wc0 = S.window_counters() if wc else None
     elapsed = max_over_ranks(timed())
     wc1 = S.window_counters() if wc else None
     progress(f"{args.config}: timed region done ({elapsed / args.steps * 1e6:.1f} us/step); replays")
     own = S.own if sharded else S.pos
     end_state = (own.clone(), S.u.clone(), S.status.clone())
+    if args.dump_outputs:
+        dump_outputs(args, {"pos": own, "u": S.u, "status": S.status, "nominal": S.vel,
+                            "neighbour_count": S.nbr_count})
     if ws > 1:
         S.check_guard()
     elapsed_stats = None
@@ -473,9 +511,9 @@ def bench_lattice(args, ws, rank, local):
             S.check_guard()
         if not same:
             raise RuntimeError("the statistics replay did not repeat the timed rollout bit for bit")
-    state_sha = gather_state_sha(own, ws)
+    state_sha = gather_state_sha(own, ws) if args.full else None
     elapsed_hist = None
-    if snap is not None and chunk > 1 and args.barrier == "reference":
+    if args.full and snap is not None and chunk > 1 and args.barrier == "reference":
         # the same timed steps again with every timestep's outputs stored (u, status, nominal
         # control, neighbour count: the reference's per-step si_velocities), statistics off
         stats_keep = S.stats.clone()
@@ -497,6 +535,49 @@ def bench_lattice(args, ws, rank, local):
         solves = int(t[0]); n_total = int(t[1])
     else:
         n_total = n_local
+    comm = ("RCCL" if args.backend == "nccl" else "gloo (host-staged rehearsal)") if ws > 1 else "single-rank"
+    cull = getattr(S, "cull", None) or getattr(getattr(S, "be", None), "cull", "cells")
+    res = {
+        "metric": METRIC,
+        "value": solves / elapsed,
+        "unit": "agent-QP solves/s",
+        "n_gpus": ws,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "ms_per_step_with_stats": None if elapsed_stats is None else elapsed_stats / args.steps * 1e3,
+        "timed_region": "filter path only (stats=NULL); safety from a bit-identical statistics replay of the same "
+                        "steps" if elapsed_stats is not None else "filter path with the statistics bookkeeping",
+        "higher_is_better": True,
+        "scaling": "weak" if args.weak and ws > 1 else "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": f"{args.config}: {W}x{rows_total} jittered lattice swarm (spacing {args.spacing}), "
+                               + (f"lattice-Laplacian consensus (gain {args.gain})" if args.nominal is None else
+                                  f"random-walk nominal control (amplitude {args.nominal[1]}, CBF_NOMINAL_RANDOM)")
+                               + (" + radius-0.2 lattice-window cull" if cull == "window" else
+                                  " + radius-0.2 cell-list cull")
+                               + " + CBF QP + clip + Euler, one fused timestep per step",
+                   "barrier": args.barrier,
+                   "cull": cull,
+                   "agents_total": n_total, "agents_per_gpu": n_local,
+                   "parallelism": (f"row-stripe shards x{ws} ({rows} rows each), one {comm} "
+                                   + ("all-to-all (ghost rows to the 2 neighbours + guard records to all)"
+                                      if args.exchange == "neighbour" else "all-gather of ghost-row slabs")
+                                   + f" per {k} steps ({halo * k} ghost rows per side)") if sharded else "single GPU",
+                   "exchange_bytes_per_rank": S.exchange_bytes() if sharded else 0,
+                   "solve_placement": ("inline in the filter" if solves_inline(S.params.c() if sharded else S.cp, rows * W)
+                                       else "queued (k_lattice_filter_hard)")
+                                      + (" (sharded: decided per sub-step window, its ghost rows included)"
+                                         if sharded else ""),
+                   "graph": use_graph,
+                   "timesteps_per_call": max(plan) if chunk > 1 else 1},
+        "timesteps_per_s": args.steps / elapsed,
+        "solves_per_step": solves / args.steps,
+    }
+    if not args.full:
+        return res
     # the timed rollout's safety record, before the kernel-timing launches below add to it
     stat = S.stats_summary()
     if ws > 1:
@@ -537,13 +618,11 @@ def bench_lattice(args, ws, rank, local):
                     "note": "pack + collective + unpack/guard, each closed by a device synchronize, mean of 10 "
                             "exchanges timed after the rollout (state restored); the timed steps overlap none of "
                             "it with compute, so it is part of ms_per_step"}
-    comm = ("RCCL" if args.backend == "nccl" else "gloo (host-staged rehearsal)") if ws > 1 else "single-rank"
     # dominant kernel (filter + clip + Euler) timed alone with HIP events on the launch stream
     S.collect_stats = modes[0]  # as in the timed region
     # the dominant kernel (k_lattice_filter) alone: an event recorded by the advance call between
     # it and the queued-QP kernel, on their launch stream (reference barrier)
     marked = args.barrier == "reference"
-    cull = getattr(S, "cull", None) or getattr(getattr(S, "be", None), "cull", "cells")
     kt = []
     # the GPU is kept busy (a spin kernel) while the host enqueues the start event and the advance,
     # so the events time the kernels and not the host's launch latency (a 20-us window-cull build
@@ -589,50 +668,13 @@ def bench_lattice(args, ws, rank, local):
     traffic = load_pmc_traffic(args.config, adv_kernels[:1]) if args.barrier == "reference" else \
         load_pmc_traffic(args.config + "_hocbf", ("k_lattice_filter_hocbf", "k_lattice_filter_hocbf_rest"))
     traffic_adv = load_pmc_traffic(args.config, adv_kernels) if args.barrier == "reference" else traffic
-    res = {
-        "metric": METRIC,
-        "value": solves / elapsed,
-        "unit": "agent-QP solves/s",
-        "n_gpus": ws,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "ms_per_step_with_stats": None if elapsed_stats is None else elapsed_stats / args.steps * 1e3,
+    res.update({
         "ms_per_step_outputs_every_step": None if elapsed_hist is None else elapsed_hist / args.steps * 1e3,
         "outputs_every_step_note": "the timed steps replayed with every timestep's filtered control, status, nominal "
                                    "control and neighbour count stored (cbf_lattice_run_ex CBF_RUN_OUTPUT_HISTORY: "
                                    "the reference's per-step si_velocities); the headline run stores positions every "
                                    "timestep and the other outputs on each call's last timestep",
-        "timed_region": "filter path only (stats=NULL); safety from a bit-identical statistics replay of the same "
-                        "steps" if elapsed_stats is not None else "filter path with the statistics bookkeeping",
-        "higher_is_better": True,
-        "scaling": "weak" if args.weak and ws > 1 else "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
         "end_state_sha256": state_sha,
-        "config": {"workload": f"{args.config}: {W}x{rows_total} jittered lattice swarm (spacing {args.spacing}), "
-                               + (f"lattice-Laplacian consensus (gain {args.gain})" if args.nominal is None else
-                                  f"random-walk nominal control (amplitude {args.nominal[1]}, CBF_NOMINAL_RANDOM)")
-                               + (" + radius-0.2 lattice-window cull" if cull == "window" else
-                                  " + radius-0.2 cell-list cull")
-                               + " + CBF QP + clip + Euler, one fused timestep per step",
-                   "barrier": args.barrier,
-                   "cull": cull,
-                   "agents_total": n_total, "agents_per_gpu": n_local,
-                   "parallelism": (f"row-stripe shards x{ws} ({rows} rows each), one {comm} "
-                                   + ("all-to-all (ghost rows to the 2 neighbours + guard records to all)"
-                                      if args.exchange == "neighbour" else "all-gather of ghost-row slabs")
-                                   + f" per {k} steps ({halo * k} ghost rows per side)") if sharded else "single GPU",
-                   "exchange_bytes_per_rank": S.exchange_bytes() if sharded else 0,
-                   "solve_placement": ("inline in the filter" if solves_inline(S.params.c() if sharded else S.cp, rows * W)
-                                       else "queued (k_lattice_filter_hard)")
-                                      + (" (sharded: decided per sub-step window, its ghost rows included)"
-                                         if sharded else ""),
-                   "graph": use_graph,
-                   "timesteps_per_call": max(plan) if chunk > 1 else 1},
-        "timesteps_per_s": args.steps / elapsed,
-        "solves_per_step": solves / args.steps,
         "exchange": exchange,
         "feasible_fraction": safety["feasible_fraction"] if safety else None,
         "safety": safety,
@@ -665,7 +707,7 @@ def bench_lattice(args, ws, rank, local):
                                        "works against",
                      "algorithmic_bytes_per_launch": FILTER_BYTES_PER_AGENT * n_local,
                      "step_algorithmic_GBps": STEP_BYTES_PER_AGENT * n_local * args.steps / elapsed / 1e9 / ws},
-    }
+    })
     return res
 
 
@@ -677,6 +719,7 @@ def exact_qp_regime(args):
     import copy
     a = copy.copy(args)
     a.config, a.spacing, a.nominal = "cfg4r", 0.22, ("random", 1.0, args.seed)
+    a.dump_outputs = None   # the headline's
     r = bench_lattice(a, 1, 0, 0)
     sf = r["safety"]
     return {"config": "cfg4r", "workload": r["config"]["workload"], "value": r["value"], "unit": r["unit"],
@@ -702,6 +745,7 @@ def feasible_regime(args):
     import copy
     a = copy.copy(args)
     a.config, a.spacing, a.nominal = "cfg4f", 0.2, None
+    a.dump_outputs = None   # the headline's
     r = bench_lattice(a, 1, 0, 0)
     sf = r["safety"]
     return {"config": "cfg4f", "workload": r["config"]["workload"], "value": r["value"], "unit": r["unit"],
@@ -738,6 +782,9 @@ def bench_allpairs(args, ws, rank, local):
     if ws > 1:
         torch.distributed.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args, {"pos": L.pos, "u": L.u, "status": L.status, "nominal": L.vel,
+                            "neighbour_count": L.nbr_count})
     solves = L.solves_total()
     elapsed, solves = _reduce(elapsed, solves, ws)
     n = W * H
@@ -770,7 +817,8 @@ def bench_mc(args, ws, rank, local):
     for _ in range(max(1, args.warmup)):  # the same launches as a timed step
         mc.run(args.mc_inner)
     torch.cuda.synchronize()
-    snap = None if args.timed_stats else mc.snapshot()
+    # (a plain run needs no replay: the solves are counted with the statistics off too)
+    snap = mc.snapshot() if args.full and not args.timed_stats else None
     mc.reset_totals()
 
     def timed():
@@ -790,6 +838,8 @@ def bench_mc(args, ws, rank, local):
 
     elapsed, kernel_ms = timed()
     elapsed, _ = _reduce(elapsed, 0, ws)
+    if args.dump_outputs:
+        dump_outputs(args, {"pos": mc.pos})
     elapsed_stats = None
     if snap is not None:
         counts_timed = mc.totals()["calls"]
@@ -808,7 +858,7 @@ def bench_mc(args, ws, rank, local):
             raise RuntimeError("cfg5: the statistics replay did not repeat the timed rollouts bit for bit")
     tot = mc.totals()
     scen_steps = args.mc_scenarios * args.mc_inner * args.steps
-    return {"metric": METRIC, "value": tot["calls"] / elapsed, "unit": "agent-QP solves/s", "n_gpus": ws,
+    line = {"metric": METRIC, "value": tot["calls"] / elapsed, "unit": "agent-QP solves/s", "n_gpus": ws,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
             "ms_per_step_with_stats": None if elapsed_stats is None else elapsed_stats / args.steps * 1e3,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
@@ -825,6 +875,9 @@ def bench_mc(args, ws, rank, local):
                        "max_violation_original_rows_relaxed": tot["max_violation_original_rows_relaxed"],
                        "min_pairwise_distance": tot["min_pairwise_distance"]},
             "roofline": mc_roofline(kernel_ms, args.mc_scenarios // ws, args.mc_inner)}
+    if not (args.full or args.timed_stats):
+        line["safety"] = None   # no statistics ran: the counters alone (value, feasible_fraction)
+    return line
 
 
 def mc_roofline(kernel_ms, n_scen, inner):
@@ -898,6 +951,8 @@ def bench_cert(args, ws, rank, local):
     if ws > 1:
         torch.distributed.barrier()
     elapsed, _ = _reduce(time.perf_counter() - t0, 0, ws)
+    if args.dump_outputs:
+        dump_outputs(args, r)
     st = r["status"].cpu().numpy()
     na = r["n_active"].cpu().numpy()
     it = r["iters"].cpu().numpy()
@@ -944,8 +999,15 @@ def main():
     ap.add_argument("--mc-inner", type=int, default=10, help="cfg5: timesteps per bench step")
     ap.add_argument("--gpus", type=int, default=1,
                     help="ranks, one per GPU (without torchrun, bench.py starts them itself)")
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps")
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="every record beside the headline: the per-step-outputs replay, kernel / roofline "
+                         "timings, the full-size check, the cfg4f / cfg4r regimes, the exchange timing, the "
+                         "end-state digest, the CPU baseline (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step computed as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB; --gpus 1)")
     ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--rows", type=int, default=1024,
                     help="lattice rows: of the whole lattice, split over the ranks (strong scaling, default), "
@@ -956,13 +1018,13 @@ def main():
     ap.add_argument("--timed-stats", action="store_true",
                     help="cfg4: keep the rollout statistics inside the timed region (default: a bit-identical "
                          "statistics replay after it)")
-    ap.add_argument("--kernel-iters", type=int, default=20)
+    ap.add_argument("--kernel-iters", type=int, default=20, help="--full: launches of the kernel timing")
     ap.add_argument("--chunk", type=int, default=50,
                     help="timesteps per cbf_lattice_run call (single-GPU graph path; 1 = one cbf_lattice_step per step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-exact-qp", action="store_true",
-                    help="cfg4 single GPU: skip the feasible_regime / exact_qp_regime records (cfg4f, cfg4r timed "
-                         "beside the headline)")
+                    help="--full, cfg4 single GPU: skip the feasible_regime / exact_qp_regime records (cfg4f, "
+                         "cfg4r timed beside the headline)")
     ap.add_argument("--cull", default="auto", choices=["auto", "cells", "window"],
                     help="single-GPU lattice cull: auto = the lattice-window cull for the consensus lattice "
                          "(cfg4, cfg4f), the cell list for cfg4r's random walk")
@@ -993,6 +1055,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.dump_outputs and args.gpus > 1:
+        raise SystemExit("bench.py: --dump-outputs writes one rank's arrays (--gpus 1)")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: this process starts the ranks and relays rank 0's line (it never touches the GPU)
         sys.exit(launch_ranks(args.gpus, sys.argv[1:],
@@ -1043,7 +1107,7 @@ def main():
         res = bench_cert(args, ws, rank, local)
     else:
         res = bench_lattice(args, ws, rank, local)
-        if args.config == "cfg4" and ws == 1 and not args.shard and args.barrier == "reference" and \
+        if args.full and args.config == "cfg4" and ws == 1 and not args.shard and args.barrier == "reference" and \
                 not args.no_exact_qp:
             res["feasible_regime"] = feasible_regime(args)
             res["exact_qp_regime"] = exact_qp_regime(args)
@@ -1057,7 +1121,7 @@ def main():
     if rank == 0:
         sample = res.pop("_cert_sample", None)
         res["cpu_baseline"] = None
-        if ws == 1 and not args.no_cpu_baseline:
+        if args.full and ws == 1 and not args.no_cpu_baseline:
             progress("CPU baseline (oracle/, after the timed region)")
             res["cpu_baseline"] = cpu_baseline_for(args, sample)
         json_out.write(json.dumps(res) + "\n")

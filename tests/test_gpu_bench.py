@@ -12,21 +12,52 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
         "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"}
+# a plain run (no --full): the headline and what it is made of
+PLAIN_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype",
+              "config"}
 
 
-def _bench(*args, n=1, steps=3):
+def _bench(*args, n=1, steps=3, full=True):
+    """One bench.py run of a 256 x 256 lattice; full: with --full (every record beside the headline)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT="29561")
+    more = ["--full", "--kernel-iters", "2", "--no-cpu-baseline"] if full else []
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--width", "256", "--rows", "256",
-                        "--steps", str(steps), "--warmup", "1", "--kernel-iters", "2", "--no-cpu-baseline", *args],
+                        "--steps", str(steps), "--warmup", "1", *more, *args],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=170)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = r.stdout.splitlines()
     assert len(lines) == 1, r.stdout[-2000:]
     res = json.loads(lines[0])
-    assert KEYS <= set(res)
+    assert (KEYS if full else PLAIN_KEYS) <= set(res)
     assert res["value"] > 0 and res["n_gpus"] == n and res["steps"] == steps
     return res
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_headline_only_and_dump_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line without the records that take runs of their
+    own, and --dump-outputs writes the arrays its last timed step left: those of the same
+    timesteps (warm-up + steps) of the same seeded lattice taken through LatticeSwarm.run directly,
+    bit for bit."""
+    import numpy as np
+    from cbf_amd import scenarios, swarm
+    steps = 7
+    res = _bench("--dump-outputs", str(tmp_path), steps=steps, full=False)
+    assert res["ms_per_step"] > 0 and res["config"]["cull"] == "window"
+    assert not {"roofline", "full_size_check", "feasible_regime", "exact_qp_regime", "safety",
+                "ms_per_step_outputs_every_step"} & set(res)
+    assert res.get("cpu_baseline") is None
+    L = swarm.LatticeSwarm(scenarios.lattice(256, 256, seed=0), 256, 256, gain=scenarios.LATTICE_GAIN, cull="window")
+    L.collect_stats = False
+    L.run(1)
+    L.run(steps)
+    want = {"pos": L.pos, "u": L.u, "status": L.status, "nominal": L.vel, "neighbour_count": L.nbr_count}
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(k + ".npy" for k in want)
+    for name, t in want.items():
+        a = np.load(tmp_path / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and a.shape == tuple(t.shape)
+        assert np.array_equal(a, t.cpu().numpy().astype(a.dtype)), name
 
 
 @pytest.mark.gpu

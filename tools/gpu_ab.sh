@@ -12,6 +12,6 @@ for t in . "$@"; do
   done
 done
 done
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/prof_cfg4 -o run -- python bench.py --steps 30 --warmup 5 --no-cpu-baseline --kernel-iters 5 > $O/prof.log 2>&1 || exit 3
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/prof_cfg4f -o run -- python bench.py --config cfg4f --steps 30 --warmup 5 --no-cpu-baseline --kernel-iters 5 > $O/prof.log 2>&1 || exit 4
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/prof_cfg4 -o run -- python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --kernel-iters 5 > $O/prof.log 2>&1 || exit 3
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/prof_cfg4f -o run -- python bench.py --config cfg4f --steps 30 --warmup 5 --full --no-cpu-baseline --kernel-iters 5 > $O/prof.log 2>&1 || exit 4
 cat $O/ab.txt

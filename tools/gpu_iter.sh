@@ -25,10 +25,10 @@ if [ -d tools/_abt/base ]; then
   grep run $O/ab_walk.txt
 fi
 for rep in $(seq 1 ${BENCH_REPS:-1}); do
-  timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench$rep.json 2> $O/bench$rep.err || { tail $O/bench$rep.err; exit 4; }
+  timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $O/bench$rep.json 2> $O/bench$rep.err || { tail $O/bench$rep.err; exit 4; }
   python -c "import json; d=json.load(open('$O/bench$rep.json')); print('bench', round(d['ms_per_step']*1e3, 2), 'tile', round(d['roofline']['kernel_ms']*1e3, 2), 'cfg4r', round(d['exact_qp_regime']['ms_per_step']*1e3, 2), d.get('end_state_sha256', '')[:8])"
 done
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/trace -o run -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/trace.log 2>&1 || { tail $O/trace.log; exit 5; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $O/trace -o run -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $O/trace.log 2>&1 || { tail $O/trace.log; exit 5; }
 f=$(find $O/trace -name '*kernel_stats.csv' | head -1); cp $f $O/kernel_stats.csv
 cut -d, -f1-4 $O/kernel_stats.csv | sed 's/(.*)"/"/' | head -12
 echo ITER_OK
