@@ -1011,7 +1011,10 @@ __device__ __forceinline__ void hocbf_hard_block(
     const int nq = nq0 < qcap ? nq0 : (int)qcap;
     const int need = (nq + 63) / 64;
     const int nwork = need < kHocbfHardPerQ ? need : kHocbfHardPerQ;
-    if (kb >= nwork) return;
+    if (kb >= nwork) {  // idle: its extents record is still finalised
+        if (ext_part) wave_extents_none(ext_part, bid);
+        return;
+    }
     int done = 0;
     if (lane == 0) done = atomicAdd(&hq[32 * (1 + kSubQ + q)], 1);
     for (int i = kb * 64 + lane; i < nq; i += nwork * 64) {
@@ -1069,7 +1072,10 @@ __device__ __forceinline__ void hocbf_wide_block(
     const int nq0 = hardq[32 * (1 + q)];
     const int nq = nq0 < qcap ? nq0 : (int)qcap;  // (a full sub-queue's counter runs past qcap: subq_append)
     const int nwork = nq < kWidePerQ ? nq : kWidePerQ;
-    if (k >= nwork) return;
+    if (k >= nwork) {  // idle: its extents record is still finalised
+        if (ext_part) wave_extents_none(ext_part, bid);
+        return;
+    }
     int done = 0;
     if (lane == 0) done = atomicAdd(&hardq[32 * (1 + kSubQ + q)], 1);
     for (int it = k; it < nq; it += nwork) {

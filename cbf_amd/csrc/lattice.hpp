@@ -66,6 +66,19 @@ __device__ __forceinline__ void wave_extents(double e0, double e1, double e2, do
     }
 }
 
+// The record of a wave that saw no owned agent (the identity of the reduction): the extents are
+// finalised over every record of the launch, so a wave that leaves early must still write its own
+// (the area is not initialised: it holds zeros, or an earlier call's records).
+__device__ __forceinline__ void wave_extents_none(double* part, long wave) {
+    if ((threadIdx.x & 63) == 0) {
+        double* o = part + 4 * wave;
+        o[0] = INFINITY;
+        o[1] = -INFINITY;
+        o[2] = -INFINITY;
+        o[3] = INFINITY;
+    }
+}
+
 __device__ __forceinline__ void ext_accumulate(int r, int row_begin, int row_end, int guard_rows, double ny,
                                                double& e0, double& e1, double& e2, double& e3) {
     e0 = pmin(e0, ny);
@@ -281,13 +294,7 @@ __device__ __forceinline__ void lattice_error_tail(int W, int row_begin, int row
         }
     }
     if (stats && slot == 0) atomicAdd(&stats[CBF_STAT_ERRORS], 1ull);
-    if (ext_part && (threadIdx.x & 63) == 0) {
-        double* o = ext_part + 4 * wave;
-        o[0] = INFINITY;
-        o[1] = -INFINITY;
-        o[2] = -INFINITY;
-        o[3] = INFINITY;
-    }
+    if (ext_part) wave_extents_none(ext_part, wave);
 }
 
 // Per-lane status counts and violation maxima of a queue kernel, summed over the wave (every lane
