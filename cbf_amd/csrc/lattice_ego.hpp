@@ -282,11 +282,14 @@ __device__ __forceinline__ void ego_finish(const KP& P, Ego& E, int w, int k, in
 }
 
 // The lattice-window cull (window.hip, CBF_RUN_WINDOW_CULL).  Geometry of a call: arrays of `rows`
-// lattice rows from lattice row row0 of a W x Hl lattice, candidates in window rows [cr0, cr1).
+// lattice rows from lattice row row0 of a W x Hl lattice, candidates in window rows [cr0, cr1): all
+// but the first and the last window row, which are candidates only at a lattice edge.
 struct WinGeom {
     int W, rows, row0, Hl, cr0, cr1;
 };
-inline WinGeom whole_lattice(int W, int H) { return WinGeom{W, H, 0, H, 0, H}; }
+inline WinGeom window_geom(int W, int H, int win_row0, int win_rows) {
+    return WinGeom{W, win_rows, win_row0, H, win_row0 > 0 ? 1 : 0, win_row0 + win_rows < H ? win_rows - 1 : win_rows};
+}
 // whether a call of this geometry can use it (rows of 4 .. 2048 agents, guard arrays in the
 // workspace's record area)
 bool window_cull_ok(int W, int rows, long n_ws, const CellWs& Wk);

@@ -3,6 +3,7 @@
 //   Euler                                        cross_and_rescue.py:173
 //   whole timestep of a lattice swarm            SURVEY cfg3/cfg4 (cross_and_rescue.py:97-175 shape)
 #include <hip/hip_ext.h>
+#include <algorithm>
 #include "cbf_device.hpp"
 #include "cells.hpp"
 #include "lattice.hpp"
@@ -552,26 +553,6 @@ __global__ void __launch_bounds__(kFinBlock) k_extents_finalize(int nparts, cons
     }
 }
 
-__global__ void k_halo_guard(const double* __restrict__ E, long stride, int ws, int rank, double radius,
-                             int32_t* __restrict__ flag) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const double rm = radius * (1.0 + 1e-9) + 1e-12;
-    const double* me = E + (long)rank * stride;
-    const double ymin = me[0], ymax = me[1];
-    int bad = 0;
-    for (int q = 0; q < ws; ++q) {
-        const double* o = E + (long)q * stride;
-        if (q < rank) {  // rows below: rank-1's rows outside our halo, everything of lower ranks
-            const double lim = (q == rank - 1) ? o[2] : o[1];
-            if (!(ymin - lim > rm)) bad = 1;
-        } else if (q > rank) {
-            const double lim = (q == rank + 1) ? o[3] : o[0];
-            if (!(lim - ymax > rm)) bad = 1;
-        }
-    }
-    if (bad) flag[0] |= 1;
-}
-
 }  // namespace
 
 namespace cbf {
@@ -579,14 +560,6 @@ void launch_extents_finalize(int nparts, const double* part, double* out, hipStr
     hipLaunchKernelGGL(k_extents_finalize, dim3(1), dim3(kFinBlock), 0, s, nparts, part, out);
 }
 }  // namespace cbf
-
-extern "C" int cbf_halo_guard(const double* ext_all, int64_t stride, int32_t world_size, int32_t rank, double radius,
-                              int32_t* flag, void* stream) {
-    if (!ext_all || !flag || world_size < 1 || rank < 0 || rank >= world_size || stride < 4) return CBF_EINVAL;
-    hipLaunchKernelGGL(k_halo_guard, dim3(1), dim3(64), 0, (hipStream_t)stream, ext_all, (long)stride, world_size,
-                       rank, radius, flag);
-    return (int)hipGetLastError();
-}
 
 extern "C" int cbf_consensus_csr(int32_t n_dst, int32_t self_offset, int32_t n_group, const double* src,
                                  const double* anchors, const int32_t* row_ptr, const int32_t* col, int32_t rotate,
@@ -705,16 +678,24 @@ static ChainSpec make_chain(const cbf_grid* grid, int W, int H, int w0, int nw0,
     return C;
 }
 
+// The optional parts of a lattice_advance.
+struct AdvanceOpts {
+    const ChainSpec* chain = nullptr;  // bin the new positions into this next build (null: no chaining)
+    bool inner = false;                // a timestep inside a run / cycle: u and status may be null
+    // filter_done alone: recorded after the filter launch; with filter_start (the measurement hook):
+    // the pair carries the filter dispatch's own start / end
+    hipEvent_t filter_start = nullptr, filter_done = nullptr;
+};
+
 static int lattice_advance(const cbf_params* p, const cbf_grid* grid, int32_t W, int32_t H, int32_t row_begin,
                            int32_t row_end, int32_t win_row0, int32_t win_rows, const double* pos, double T,
                            double* pos_out, double* u, int32_t* status, int32_t* nbr_count, int32_t guard_rows,
                            double* extents, uint64_t* stats, void* workspace, size_t workspace_bytes,
-                           int32_t cnt_begin, int32_t cnt_end, void* stream, const ChainSpec* chain = nullptr,
-                           bool inner = false, hipEvent_t filter_done = nullptr,
-                           hipEvent_t filter_start = nullptr) {
+                           int32_t cnt_begin, int32_t cnt_end, void* stream, const AdvanceOpts& opt = {}) {
     int rc = check_lattice(p, grid, W, H, row_begin, row_end, win_row0, win_rows, pos, workspace, workspace_bytes);
     if (rc) return rc;
-    if (!pos_out || (!inner && (!u || !status))) return CBF_EINVAL;  // inner: a cbf_lattice_run timestep
+    if (!pos_out || (!opt.inner && (!u || !status))) return CBF_EINVAL;
+    const ChainSpec chain = opt.chain ? *opt.chain : ChainSpec{};
     hipStream_t s = (hipStream_t)stream;
     const long n = (long)W * win_rows;
     const CellGrid G = make_grid(grid);
@@ -737,18 +718,17 @@ static int lattice_advance(const cbf_params* p, const cbf_grid* grid, int32_t W,
                  : (p->f_is_zero ? k_lattice_filter<true, false, true> : k_lattice_filter<false, false, true>))
            : (st ? (p->f_is_zero ? k_lattice_filter<true, true, false> : k_lattice_filter<false, true, false>)
                  : (p->f_is_zero ? k_lattice_filter<true, false, false> : k_lattice_filter<false, false, false>));
-    if (filter_start) {  // the measurement hook: events carrying the filter dispatch's own start / end
-        hipExtLaunchKernelGGL(filter, dim3(nb), dim3(kBlock), 0, s, filter_start, filter_done, 0u,
+    if (opt.filter_start) {
+        hipExtLaunchKernelGGL(filter, dim3(nb), dim3(kBlock), 0, s, opt.filter_start, opt.filter_done, 0u,
                               kp, G, B, W, row_begin, row_end, win_row0, n, Wk.ncell, Wk.spos, Wk.svel, Wk.sidx,
                               Wk.start, Wk.sctl, T, po, uo, status, nbr_count, ext_part, st, Wk.hardq, Wk.qrec,
-                              Wk.qcap, chain ? *chain : ChainSpec{});
+                              Wk.qcap, chain);
     } else {
         hipLaunchKernelGGL(filter, dim3(nb), dim3(kBlock), 0, s,
                            kp, G, B, W, row_begin, row_end, win_row0, n, Wk.ncell, Wk.spos, Wk.svel, Wk.sidx, Wk.start,
-                           Wk.sctl, T, po, uo, status, nbr_count, ext_part, st, Wk.hardq, Wk.qrec, Wk.qcap,
-                           chain ? *chain : ChainSpec{});
-        if (filter_done)
-            if (hipError_t e = hipEventRecord(filter_done, s)) return (int)e;
+                           Wk.sctl, T, po, uo, status, nbr_count, ext_part, st, Wk.hardq, Wk.qrec, Wk.qcap, chain);
+        if (opt.filter_done)
+            if (hipError_t e = hipEventRecord(opt.filter_done, s)) return (int)e;
     }
     if (in) {
         if (extents) launch_extents_finalize((int)lattice_ext_waves(n), ext_part, extents, s);
@@ -757,7 +737,7 @@ static int lattice_advance(const cbf_params* p, const cbf_grid* grid, int32_t W,
     hipLaunchKernelGGL(k_lattice_filter_hard, dim3(hb), dim3(64), 0, s,
                        kp, G, B, T, po, uo, status, nbr_count,
                        ext_part ? ext_part + 4l * lattice_ext_waves(n) : nullptr, st, Wk.hardq, Wk.qrec, Wk.qcap,
-                       chain ? *chain : ChainSpec{}, Wk.sctl);
+                       chain, Wk.sctl);
     if (extents) launch_extents_finalize((int)lattice_ext_waves(n) + hb, ext_part, extents, s);
     return (int)hipGetLastError();
 }
@@ -781,8 +761,8 @@ extern "C" int cbf_lattice_advance_marked(const cbf_params* p, const cbf_grid* g
                                           int32_t* nbr_count, int32_t guard_rows, double* extents, uint64_t* stats,
                                           void* workspace, size_t workspace_bytes, void* filter_done, void* stream) {
     return lattice_advance(p, grid, W, H, row_begin, row_end, win_row0, win_rows, pos, T, pos_out, u, status, nbr_count,
-                           guard_rows, extents, stats, workspace, workspace_bytes, row_begin, row_end, stream, nullptr,
-                           false, (hipEvent_t)filter_done);
+                           guard_rows, extents, stats, workspace, workspace_bytes, row_begin, row_end, stream,
+                           {.filter_done = (hipEvent_t)filter_done});
 }
 
 extern "C" int cbf_lattice_advance_timed(const cbf_params* p, const cbf_grid* grid, int32_t W, int32_t H,
@@ -793,8 +773,8 @@ extern "C" int cbf_lattice_advance_timed(const cbf_params* p, const cbf_grid* gr
                                          void* filter_stop, void* stream) {
     if (!filter_start || !filter_stop) return CBF_EINVAL;
     return lattice_advance(p, grid, W, H, row_begin, row_end, win_row0, win_rows, pos, T, pos_out, u, status, nbr_count,
-                           guard_rows, extents, stats, workspace, workspace_bytes, row_begin, row_end, stream, nullptr,
-                           false, (hipEvent_t)filter_stop, (hipEvent_t)filter_start);
+                           guard_rows, extents, stats, workspace, workspace_bytes, row_begin, row_end, stream,
+                           {.filter_start = (hipEvent_t)filter_start, .filter_done = (hipEvent_t)filter_stop});
 }
 
 extern "C" int cbf_lattice_step(const cbf_params* p, const cbf_grid* grid, int32_t W, int32_t H, int32_t row_begin,
@@ -818,18 +798,36 @@ static void launch_hard_plain(const cbf_params* p, const cbf_grid* grid, const C
                        make_grid(grid), B, T, pos_out, u, status, cnt, (double*)nullptr, stats, Wk.hardq, Wk.qrec,
                        Wk.qcap, ChainSpec{}, Wk.sctl);
 }
-static void launch_hard_plain(const cbf_params* p, const cbf_grid* grid, const CellWs& Wk, int W, int H, double T,
-                              double2* pos_out, double2* u, int32_t* status, int32_t* cnt, unsigned long long* stats,
-                              hipStream_t s) {
-    const long n = (long)W * H;
-    launch_hard_plain(p, grid, Wk, make_win_bounds(W, 0, n, 0, H, 0, H, 0), n, T, pos_out, u, status, cnt, stats, s);
+
+// The per-agent outputs (nominal / filtered control, status, count) of one timestep of a run or
+// cycle: those of the last step only (the earlier ones' would be overwritten there), or of every
+// step into its slice of the history arrays -- agent offset o either way -- or none (all null).
+struct StepOut {
+    double *vel = nullptr, *u = nullptr;
+    int32_t *status = nullptr, *cnt = nullptr;
+    double2* vel2() const { return reinterpret_cast<double2*>(vel); }
+    double2* u2() const { return reinterpret_cast<double2*>(u); }
+};
+static StepOut step_out(bool on, double* vel, double* u, int32_t* status, int32_t* cnt, long o) {
+    return on ? StepOut{vel + 2 * o, u + 2 * o, status + o, cnt ? cnt + o : nullptr} : StepOut{};
 }
+
+// Position buffers of a window-cull loop of n steps.  The filter reads its input positions while
+// writing new ones, so the steps alternate between the caller's array a and scratch b such that the
+// last step writes a: with an odd n step 0 reads b, and its build -- which reads a -- copies a to b.
+struct PingPong {
+    double2* buf[2];
+    int odd;
+    PingPong(double2* a, double2* b, int n) : buf{a, b}, odd(n & 1) {}
+    double2* src(int j) const { return buf[(j + odd) & 1]; }
+    double2* dst(int j) const { return buf[(j + 1 + odd) & 1]; }
+    bool first_copies(int j) const { return j == 0 && odd; }
+    double2* build_src(int j) const { return first_copies(j) ? buf[0] : src(j); }
+};
 
 // cbf_lattice_run_ex with CBF_RUN_WINDOW_CULL: per timestep the window build (k_window_prep:
 // nominal controls and the guards), the window filter and, for a large window, the queued-QP
-// kernel.  The filter reads its input positions while writing new ones, so timesteps alternate
-// between pos and the workspace's spos: with an odd count the first build also copies pos to spos
-// and the first filter reads that copy, so the last timestep always writes pos.
+// kernel, between pos and the workspace's spos (PingPong).
 static int lattice_run_window(const cbf_params* p, const cbf_grid* grid, int32_t W, int32_t H, double* pos,
                               double gain, double T, int32_t steps, double* vel_out, double* u, int32_t* status,
                               int32_t* nbr_count, uint64_t* stats, void* workspace, bool hist, void* stream) {
@@ -838,23 +836,18 @@ static int lattice_run_window(const cbf_params* p, const cbf_grid* grid, int32_t
     CellWs Wk(workspace, n, (long)grid->nx * grid->ny);
     if (!window_cull_ok(W, H, n, Wk)) return CBF_EINVAL;
     const bool in = solve_inline(p, n);
-    double2* buf[2] = {reinterpret_cast<double2*>(pos), Wk.spos};
-    const int odd = steps & 1;
+    const PingPong pp(reinterpret_cast<double2*>(pos), Wk.spos, steps);
+    const WinGeom Q = window_geom(W, H, 0, H);
     unsigned long long* st = reinterpret_cast<unsigned long long*>(stats);
     for (int k = 0; k < steps; ++k) {
-        double2* src = buf[(k + odd) & 1];
-        double2* dst = buf[(k + 1 + odd) & 1];
-        const bool last = k + 1 == steps, out = last || hist;
-        const long o = hist ? (long)k * n : 0;
-        // an odd run's first build reads pos and leaves its copy in spos, which the filter then reads
-        const WinGeom Q = whole_lattice(W, H);
-        window_prep(Wk, Q, k == 0 && odd ? buf[0] : src, gain, out ? reinterpret_cast<double2*>(vel_out) + o : nullptr,
-                    k == 0 && odd ? buf[1] : nullptr, nullptr, 0, H, ExtSpec{0, 0, 0}, window_fold(p), s);
-        double2* uo = out ? reinterpret_cast<double2*>(u) + o : nullptr;
-        int32_t* so = out ? status + o : nullptr;
-        int32_t* co = out && nbr_count ? nbr_count + o : nullptr;
-        window_filter(p, Wk, Q, 0, H, 0, H, src, T, dst, uo, so, co, st, in, s);
-        if (!in) launch_hard_plain(p, grid, Wk, W, H, T, dst, uo, so, co, st, s);
+        double2 *src = pp.src(k), *dst = pp.dst(k);
+        const StepOut O = step_out(k + 1 == steps || hist, vel_out, u, status, nbr_count, hist ? (long)k * n : 0);
+        window_prep(Wk, Q, pp.build_src(k), gain, O.vel2(), pp.first_copies(k) ? src : nullptr, nullptr, 0, H,
+                    ExtSpec{0, 0, 0}, window_fold(p), s);
+        window_filter(p, Wk, Q, 0, H, 0, H, src, T, dst, O.u2(), O.status, O.cnt, st, in, s);
+        if (!in)
+            launch_hard_plain(p, grid, Wk, make_win_bounds(W, 0, n, 0, H, 0, H, 0), n, T, dst, O.u2(), O.status, O.cnt,
+                              st, s);
         if (int rc = (int)hipGetLastError()) return rc;
     }
     return 0;
@@ -864,11 +857,6 @@ static int lattice_run_window(const cbf_params* p, const cbf_grid* grid, int32_t
 // times the filter kernel alone), for the owned rows [row_begin, row_end) of a window of win_rows
 // lattice rows from win_row0 (the whole lattice, or a sharded sub-step's window).  pos_out (index
 // (r - row_begin) W + c) must not overlap pos.
-static WinGeom window_geom(int W, int H, int win_row0, int win_rows) {
-    return WinGeom{W, win_rows, win_row0, H, win_row0 > 0 ? 1 : 0,
-                   win_row0 + win_rows < H ? win_rows - 1 : win_rows};
-}
-
 extern "C" int cbf_lattice_window_build_ex(const cbf_params* p, const cbf_grid* grid, int32_t W, int32_t H,
                                            int32_t row_begin, int32_t row_end, int32_t win_row0, int32_t win_rows,
                                            const double* pos, double gain, double* vel_out, void* workspace,
@@ -978,17 +966,14 @@ extern "C" int cbf_lattice_run_ex(const cbf_params* p, const cbf_grid* grid, int
             hipLaunchKernelGGL(k_lattice_nominal_bin_ordered, dim3(nblk(n)), dim3(kBlock), 0, s, G, W, H, 0, H, 0, H,
                                p2, Wk.count, Wk.sidx, Wk.start, Wk.ncell, lattice_bcs(Wk), Wk.hardq,
                                (unsigned long long*)nullptr, ExtSpec{0, 0, 0}, Wk.sctl);
-        // vel_out, u, status and nbr_count are written by the last timestep only (the inner ones'
-        // would be overwritten), or by every timestep into its slice of the history arrays
         const bool last = k + 1 == steps, out = last || hist;
-        const long o = hist ? (long)k * n : 0;
-        lattice_scan_scatter(Wk, W, H, 0, H, 0, n, p2, gain, out ? vel_out + 2 * o : nullptr, s);
+        const StepOut O = step_out(out, vel_out, u, status, nbr_count, hist ? (long)k * n : 0);
+        lattice_scan_scatter(Wk, W, H, 0, H, 0, n, p2, gain, O.vel, s);
         rc = (int)hipGetLastError();
         if (rc) return rc;
         const ChainSpec C = make_chain(grid, W, H, 0, 0, H, workspace);
-        rc = lattice_advance(p, grid, W, H, 0, H, 0, H, pos, T, pos, out ? u + 2 * o : nullptr,
-                             out ? status + o : nullptr, out && nbr_count ? nbr_count + o : nullptr, 0, nullptr,
-                             stats, workspace, workspace_bytes, 0, H, stream, last ? nullptr : &C, !out);
+        rc = lattice_advance(p, grid, W, H, 0, H, 0, H, pos, T, pos, O.u, O.status, O.cnt, 0, nullptr, stats, workspace,
+                             workspace_bytes, 0, H, stream, {.chain = last ? nullptr : &C, .inner = !out});
         if (rc) return rc;
     }
     return 0;
@@ -1002,6 +987,62 @@ extern "C" int cbf_lattice_run(const cbf_params* p, const cbf_grid* grid, int32_
                               workspace_bytes, 0u, stream);
 }
 
+// Geometry of sub-step k of an exchange cycle of nsub (cbf_amd/shard.py: Sub): computed rows
+// [a, b), window rows [w0, w1), guard rows.
+struct SubStep {
+    int a, b, w0, w1, guard;
+};
+static SubStep sub_step(int own_begin, int own_end, int halo, int nsub, int H, int k) {
+    const int d = halo * (nsub - k - 1);
+    const int a = std::max(own_begin - d, 0), b = std::min(own_end + d, H);
+    return SubStep{a, b, std::max(a - halo, 0), std::min(b + halo, H), d + halo - 1};
+}
+
+// The window-cull form of an exchange cycle: per sub-step the window build (nominal controls,
+// guards, and the halo-guard extents of its input, as the cell-list bin / scatter accumulate them),
+// the window filter and the queued-QP kernel.  Sub-step s reads its window from one buffer and
+// writes the rows it computes -- exactly the next sub-step's window -- to the other: wpos and
+// workspace 0's spos (sized for the whole cycle window; PingPong).  Same results as the cell-list
+// cycle whenever its halo guard holds (the guard is the same).
+static int cycle_sharded_window(const cbf_params* p, const cbf_grid* grid, int32_t W, int32_t H, int32_t own_begin,
+                                int32_t own_end, int32_t halo, int32_t nsub, int32_t sub_begin, int32_t sub_end,
+                                int32_t win_row0, int32_t win_rows, double* wpos, double gain, double T, double* wvel,
+                                double* wu, int32_t* wstatus, int32_t* wcnt, uint64_t* ext_keys, uint64_t* stats,
+                                void* workspaces, size_t ws_bytes, hipStream_t st) {
+    const long ncell = (long)grid->nx * grid->ny;
+    const CellWs W0(workspaces, (long)W * win_rows, ncell);
+    if (!window_cull_ok(W, win_rows, (long)W * win_rows, W0)) return CBF_EINVAL;
+    const int n = sub_end - sub_begin;
+    const PingPong pp(reinterpret_cast<double2*>(wpos), W0.spos, n);
+    const size_t set_words = cbf_halo_ext_bytes(1) / 8;
+    unsigned long long* stw = reinterpret_cast<unsigned long long*>(stats);
+    for (int j = 0; j < n; ++j) {
+        const int k = sub_begin + j;
+        const SubStep S = sub_step(own_begin, own_end, halo, nsub, H, k);
+        const int rows = S.w1 - S.w0;
+        void* ws = (char*)workspaces + (size_t)k * ws_bytes;
+        int rc = check_lattice(p, grid, W, H, S.a, S.b, S.w0, rows, wpos, ws, ws_bytes);
+        if (rc) return rc;
+        const CellWs Wk(ws, (long)W * rows, ncell);
+        if (!window_cull_ok(W, rows, (long)W * rows, Wk)) return CBF_EINVAL;
+        const WinGeom Q = window_geom(W, H, S.w0, rows);
+        // the sub-step's window and its computed rows within the cycle window
+        const long wo = (long)(S.w0 - win_row0) * W, o = (long)(S.a - win_row0) * W;
+        double2 *src = pp.src(j) + wo, *dst = pp.dst(j) + o;
+        const StepOut O = step_out(j + 1 == n, wvel, wu, wstatus, wcnt, o);
+        unsigned long long* ek = reinterpret_cast<unsigned long long*>(ext_keys) + (size_t)k * set_words;
+        window_prep(Wk, Q, pp.build_src(j) + wo, gain, O.vel2(), pp.first_copies(j) ? src : nullptr, ek, S.a, S.b,
+                    ExtSpec{own_begin, own_end, S.guard}, window_fold(p), st);
+        const bool in = solve_inline(p, (long)W * rows);
+        window_filter(p, Wk, Q, S.a, S.b, own_begin, own_end, src, T, dst, O.u2(), O.status, O.cnt, stw, in, st);
+        if (!in)
+            launch_hard_plain(p, grid, Wk, make_win_bounds(W, S.w0, (long)W * rows, S.a, S.b, own_begin, own_end, 0),
+                              (long)W * rows, T, dst, O.u2(), O.status, O.cnt, stw, st);
+        if (int e = (int)hipGetLastError()) return e;
+    }
+    return 0;
+}
+
 // One exchange cycle of the row-sharded step (cbf_amd/shard.py): nsub sub-steps after the caller's
 // halo unpack, sub-step s with workspace s of `workspaces` (nsub x ws_bytes).  Sub-step 0 builds
 // its cell list from the window positions (bin kernel, guard extents of set 0); every advance but
@@ -1012,7 +1053,71 @@ static int cycle_sharded(const cbf_params* p, const cbf_grid* grid, int32_t W, i
                          int32_t own_end, int32_t halo, int32_t nsub, int32_t sub_begin, int32_t sub_end,
                          int32_t win_row0, int32_t win_rows, double* wpos, double gain, double T, double* wvel,
                          double* wu, int32_t* wstatus, int32_t* wcnt, uint64_t* ext_keys, uint64_t* stats,
-                         void* workspaces, size_t ws_bytes, bool window, void* stream);
+                         void* workspaces, size_t ws_bytes, bool window, void* stream) {
+    if (!p || !grid || W <= 0 || H <= 0 || halo < 2 || nsub < 1 || own_begin < 0 || own_end > H ||
+        own_begin >= own_end || sub_begin < 0 || sub_end > nsub || sub_begin >= sub_end)
+        return CBF_EINVAL;
+    const long G = (long)halo * nsub;
+    if (G > own_end - own_begin) return CBF_EINVAL;
+    const int w0 = (int)(own_begin - G > 0 ? own_begin - G : 0), w1 = (int)(own_end + G < H ? own_end + G : H);
+    if (win_row0 != w0 || win_rows != w1 - w0) return CBF_EINVAL;
+    if (!wpos || !wvel || !wu || !wstatus || !ext_keys || !workspaces) return CBF_EINVAL;
+    if (ws_bytes < cbf_lattice_workspace_size(W, win_rows, grid)) return CBF_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t set_words = cbf_halo_ext_bytes(1) / 8;
+    // a chained build's records are indexed by the previous sub-step's slots (12 B each; that
+    // window has up to 2 halo rows more): they must fit its record area (16 B per agent of its
+    // own window), which holds for stripes of >= 4 halo rows; checked before anything is launched
+    for (int k = 1; k < nsub; ++k) {
+        const SubStep S = sub_step(own_begin, own_end, halo, nsub, H, k);
+        const SubStep prev = sub_step(own_begin, own_end, halo, nsub, H, k - 1);
+        if (12l * (prev.w1 - prev.w0) > 16l * (S.w1 - S.w0)) return CBF_EINVAL;
+    }
+    if (window)
+        return cycle_sharded_window(p, grid, W, H, own_begin, own_end, halo, nsub, sub_begin, sub_end, win_row0,
+                                    win_rows, wpos, gain, T, wvel, wu, wstatus, wcnt, ext_keys, stats, workspaces,
+                                    ws_bytes, st);
+    for (int k = sub_begin; k < sub_end; ++k) {
+        const SubStep S = sub_step(own_begin, own_end, halo, nsub, H, k);
+        const int rows = S.w1 - S.w0;
+        void* ws = (char*)workspaces + (size_t)k * ws_bytes;
+        const bool last = k + 1 == sub_end;
+        double* spos = wpos + 2l * (S.w0 - win_row0) * W;
+        // outputs of the call's last sub-step only (its computed rows contain the owned rows; the
+        // ghost rows' are not outputs)
+        const long o = (long)(S.a - win_row0) * W;
+        const StepOut O = step_out(last, wvel, wu, wstatus, wcnt, o);
+        const ExtSpec X{own_begin, own_end, S.guard};
+        unsigned long long* ek = reinterpret_cast<unsigned long long*>(ext_keys) + (size_t)k * set_words;
+        int rc;
+        if (k == sub_begin) {  // (a vel_out whether last or not: the bin build must have one)
+            rc = lattice_build(p, grid, W, H, S.a, S.b, S.w0, rows, spos, gain, wvel + 2 * o, ws, ws_bytes, ek, X,
+                               stream);
+        } else {
+            rc = check_lattice(p, grid, W, H, S.a, S.b, S.w0, rows, spos, ws, ws_bytes);
+            if (!rc) {
+                const SubStep prev = sub_step(own_begin, own_end, halo, nsub, H, k - 1);
+                const long n = (long)W * rows, nprev = (long)W * (prev.w1 - prev.w0);
+                CellWs Wk(ws, n, (long)grid->nx * grid->ny);
+                lattice_scan_scatter(Wk, W, H, S.a, S.b, S.w0, n, reinterpret_cast<const double2*>(spos), gain, O.vel,
+                                     st, nprev, ek, X);
+                rc = (int)hipGetLastError();
+            }
+        }
+        if (rc) return rc;
+        ChainSpec C;
+        if (!last) {
+            const SubStep next = sub_step(own_begin, own_end, halo, nsub, H, k + 1);
+            C = make_chain(grid, W, H, S.w0, next.w0, next.w1 - next.w0,
+                           (char*)workspaces + (size_t)(k + 1) * ws_bytes);
+        }
+        rc = lattice_advance(p, grid, W, H, S.a, S.b, S.w0, rows, spos, T, wpos + 2 * o, O.u, O.status, O.cnt, S.guard,
+                             nullptr, stats, ws, ws_bytes, own_begin, own_end, stream,
+                             {.chain = last ? nullptr : &C, .inner = !last});
+        if (rc) return rc;
+    }
+    return 0;
+}
 
 extern "C" int cbf_lattice_cycle_sharded_ex(const cbf_params* p, const cbf_grid* grid, int32_t W, int32_t H,
                                             int32_t own_begin, int32_t own_end, int32_t halo, int32_t nsub,
@@ -1037,138 +1142,6 @@ extern "C" int cbf_lattice_cycle_sharded(const cbf_params* p, const cbf_grid* gr
                          gain, T, wvel, wu, wstatus, wcnt, ext_keys, stats, workspaces, ws_bytes, false, stream);
 }
 
-// The window-cull form of an exchange cycle: per sub-step the window build (nominal controls,
-// guards, and the halo-guard extents of its input, as the cell-list bin / scatter accumulate them),
-// the window filter and the queued-QP kernel.  Sub-step s reads its window from one buffer and
-// writes the rows it computes -- exactly the next sub-step's window -- to the other: wpos and
-// workspace 0's spos (sized for the whole cycle window), so that the call's last sub-step writes
-// wpos (with an odd count the first build copies its window to spos).  Same results as the
-// cell-list cycle whenever its halo guard holds (the guard is the same).
-template <class Sub>
-static int cycle_sharded_window(const cbf_params* p, const cbf_grid* grid, int32_t W, int32_t H, int32_t own_begin,
-                                int32_t own_end, int32_t nsub, int32_t sub_begin, int32_t sub_end, int32_t win_row0,
-                                int32_t win_rows, double* wpos, double gain, double T, double* wvel, double* wu,
-                                int32_t* wstatus, int32_t* wcnt, uint64_t* ext_keys, uint64_t* stats,
-                                void* workspaces, size_t ws_bytes, Sub&& sub, hipStream_t st) {
-    const long ncell = (long)grid->nx * grid->ny;
-    const CellWs W0(workspaces, (long)W * win_rows, ncell);
-    if (!window_cull_ok(W, win_rows, (long)W * win_rows, W0)) return CBF_EINVAL;
-    double2* buf[2] = {reinterpret_cast<double2*>(wpos), W0.spos};
-    const int n = sub_end - sub_begin, odd = n & 1;
-    const size_t set_words = cbf_halo_ext_bytes(1) / 8;
-    unsigned long long* stw = reinterpret_cast<unsigned long long*>(stats);
-    for (int j = 0; j < n; ++j) {
-        const int k = sub_begin + j;
-        int a, b, sw0, sw1, guard;
-        sub(k, a, b, sw0, sw1, guard);
-        const int rows = sw1 - sw0;
-        void* ws = (char*)workspaces + (size_t)k * ws_bytes;
-        int rc = check_lattice(p, grid, W, H, a, b, sw0, rows, wpos, ws, ws_bytes);
-        if (rc) return rc;
-        const CellWs Wk(ws, (long)W * rows, ncell);
-        if (!window_cull_ok(W, rows, (long)W * rows, Wk)) return CBF_EINVAL;
-        const WinGeom Q{W, rows, sw0, H, sw0 > 0 ? 1 : 0, sw1 < H ? rows - 1 : rows};
-        double2* src = buf[(j + odd) & 1] + (long)(sw0 - win_row0) * W;
-        double2* dst = buf[(j + 1 + odd) & 1] + (long)(a - win_row0) * W;
-        const bool last = j + 1 == n;
-        const long o = (long)(a - win_row0) * W;
-        unsigned long long* ek = reinterpret_cast<unsigned long long*>(ext_keys) + (size_t)k * set_words;
-        // an odd call's first build reads wpos and leaves the copy its filter reads in spos
-        window_prep(Wk, Q, j == 0 && odd ? buf[0] + (long)(sw0 - win_row0) * W : src, gain,
-                    last ? reinterpret_cast<double2*>(wvel) + o : nullptr, j == 0 && odd ? src : nullptr, ek, a, b,
-                    ExtSpec{own_begin, own_end, guard}, window_fold(p), st);
-        double2* uo = last ? reinterpret_cast<double2*>(wu) + o : nullptr;
-        int32_t* so = last ? wstatus + o : nullptr;
-        int32_t* co = last && wcnt ? wcnt + o : nullptr;
-        const bool in = solve_inline(p, (long)W * rows);
-        window_filter(p, Wk, Q, a, b, own_begin, own_end, src, T, dst, uo, so, co, stw, in, st);
-        if (!in)
-            launch_hard_plain(p, grid, Wk, make_win_bounds(W, sw0, (long)W * rows, a, b, own_begin, own_end, 0),
-                              (long)W * rows, T, dst, uo, so, co, stw, st);
-        if (int e = (int)hipGetLastError()) return e;
-    }
-    return 0;
-}
-
-static int cycle_sharded(const cbf_params* p, const cbf_grid* grid, int32_t W, int32_t H, int32_t own_begin,
-                         int32_t own_end, int32_t halo, int32_t nsub, int32_t sub_begin, int32_t sub_end,
-                         int32_t win_row0, int32_t win_rows, double* wpos, double gain, double T, double* wvel,
-                         double* wu, int32_t* wstatus, int32_t* wcnt, uint64_t* ext_keys, uint64_t* stats,
-                         void* workspaces, size_t ws_bytes, bool window, void* stream) {
-    if (!p || !grid || W <= 0 || H <= 0 || halo < 2 || nsub < 1 || own_begin < 0 || own_end > H ||
-        own_begin >= own_end || sub_begin < 0 || sub_end > nsub || sub_begin >= sub_end)
-        return CBF_EINVAL;
-    const long G = (long)halo * nsub;
-    if (G > own_end - own_begin) return CBF_EINVAL;
-    const int w0 = (int)(own_begin - G > 0 ? own_begin - G : 0), w1 = (int)(own_end + G < H ? own_end + G : H);
-    if (win_row0 != w0 || win_rows != w1 - w0) return CBF_EINVAL;
-    if (!wpos || !wvel || !wu || !wstatus || !ext_keys || !workspaces) return CBF_EINVAL;
-    if (ws_bytes < cbf_lattice_workspace_size(W, win_rows, grid)) return CBF_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t set_words = cbf_halo_ext_bytes(1) / 8;
-    auto sub = [&](int k, int& a, int& b, int& sw0, int& sw1, int& guard) {
-        const int d = (int)G - halo * (k + 1);
-        a = own_begin - d > 0 ? own_begin - d : 0;
-        b = own_end + d < H ? own_end + d : H;
-        sw0 = a - halo > 0 ? a - halo : 0;
-        sw1 = b + halo < H ? b + halo : H;
-        guard = d + halo - 1;
-    };
-    // a chained build's records are indexed by the previous sub-step's slots (12 B each; that
-    // window has up to 2 halo rows more): they must fit its record area (16 B per agent of its
-    // own window), which holds for stripes of >= 4 halo rows; checked before anything is launched
-    for (int k = 1; k < nsub; ++k) {
-        int a, b, w0k, w1k, g, pa, pb, pw0, pw1, pg;
-        sub(k, a, b, w0k, w1k, g);
-        sub(k - 1, pa, pb, pw0, pw1, pg);
-        if (12l * (pw1 - pw0) > 16l * (w1k - w0k)) return CBF_EINVAL;
-    }
-    if (window)
-        return cycle_sharded_window(p, grid, W, H, own_begin, own_end, nsub, sub_begin, sub_end, win_row0, win_rows,
-                                    wpos, gain, T, wvel, wu, wstatus, wcnt, ext_keys, stats, workspaces, ws_bytes,
-                                    sub, st);
-    for (int k = sub_begin; k < sub_end; ++k) {
-        int a, b, sw0, sw1, guard;
-        sub(k, a, b, sw0, sw1, guard);
-        void* ws = (char*)workspaces + (size_t)k * ws_bytes;
-        // the per-sub-step outputs (nominal / filtered control, status, count) are written by the
-        // call's last sub-step only: the earlier ones' would be overwritten there (its computed rows
-        // contain the owned rows; the ghost rows' are not outputs)
-        const bool last = k + 1 == sub_end;
-        double* spos = wpos + 2l * (sw0 - win_row0) * W;
-        const long o = (long)(a - win_row0) * W;
-        unsigned long long* ek = reinterpret_cast<unsigned long long*>(ext_keys) + (size_t)k * set_words;
-        int rc;
-        if (k == sub_begin) {
-            rc = lattice_build(p, grid, W, H, a, b, sw0, sw1 - sw0, spos, gain, wvel + 2 * o, ws, ws_bytes, ek,
-                               ExtSpec{own_begin, own_end, guard}, stream);  // (vel_out: the bin build must)
-        } else {
-            rc = check_lattice(p, grid, W, H, a, b, sw0, sw1 - sw0, spos, ws, ws_bytes);
-            if (!rc) {
-                int pa, pb, pw0, pw1, pg;
-                sub(k - 1, pa, pb, pw0, pw1, pg);
-                const long n = (long)W * (sw1 - sw0), nprev = (long)W * (pw1 - pw0);
-                CellWs Wk(ws, n, (long)grid->nx * grid->ny);
-                lattice_scan_scatter(Wk, W, H, a, b, sw0, n, reinterpret_cast<const double2*>(spos), gain,
-                                     last ? wvel + 2 * o : nullptr, st, nprev, ek, ExtSpec{own_begin, own_end, guard});
-                rc = (int)hipGetLastError();
-            }
-        }
-        if (rc) return rc;
-        ChainSpec C;
-        if (!last) {
-            int na, nb, nw0, nw1, ng;
-            sub(k + 1, na, nb, nw0, nw1, ng);
-            C = make_chain(grid, W, H, sw0, nw0, nw1 - nw0, (char*)workspaces + (size_t)(k + 1) * ws_bytes);
-        }
-        rc = lattice_advance(p, grid, W, H, a, b, sw0, sw1 - sw0, spos, T, wpos + 2 * o, last ? wu + 2 * o : nullptr,
-                             last ? wstatus + o : nullptr, last && wcnt ? wcnt + o : nullptr, guard, nullptr, stats, ws,
-                             ws_bytes, own_begin, own_end, stream, last ? nullptr : &C, !last);
-        if (rc) return rc;
-    }
-    return 0;
-}
-
 extern "C" int cbf_lattice_step_sharded(const cbf_params* p, const cbf_grid* grid, int32_t W, int32_t H,
                                         int32_t row_begin, int32_t row_end, int32_t own_begin, int32_t own_end,
                                         int32_t win_row0, int32_t win_rows, const double* pos, double gain, double T,
@@ -1183,271 +1156,4 @@ extern "C" int cbf_lattice_step_sharded(const cbf_params* p, const cbf_grid* gri
     if (rc) return rc;
     return lattice_advance(p, grid, W, H, row_begin, row_end, win_row0, win_rows, pos, T, pos_out, u, status, nbr_count,
                            guard_rows, nullptr, stats, workspace, workspace_bytes, own_begin, own_end, stream);
-}
-
-// ---- halo exchange of the row-sharded step -----------------------------------------
-namespace {
-
-__device__ __forceinline__ double dkey_inv(unsigned long long k) {
-    const unsigned long long u = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-    return __longlong_as_double((long long)u);
-}
-
-// send = [first halo rows | last halo rows | nsub records of 8 doubles (6 extents used)]; wave q
-// of block 0 (q < nsub) reduces the 64 extent-key slots of sub-step q into its record and resets
-// them for the next accumulation.
-__global__ void __launch_bounds__(kBlock) k_halo_pack(int W, int halo, long n_own, const double2* __restrict__ own,
-                                                      unsigned long long* __restrict__ keys, int nsub,
-                                                      double* __restrict__ send) {
-    const long t = (long)blockIdx.x * kBlock + threadIdx.x;
-    const long rs = (long)halo * W;
-    double2* s2 = reinterpret_cast<double2*>(send);
-    if (t < rs) s2[t] = own[t];
-    else if (t < 2 * rs) s2[t] = own[n_own - 2 * rs + t];
-    if (blockIdx.x == 0) {
-        const int l = threadIdx.x & 63;
-        for (int q = threadIdx.x >> 6; q < nsub; q += kBlock / 64) {
-            unsigned long long k[kExtVals];
-#pragma unroll
-            for (int v = 0; v < kExtVals; ++v) k[v] = dkey(ext_is_min(v) ? INFINITY : -INFINITY);
-            for (int j = l; j < kExtSlots; j += 64) {
-                unsigned long long* kl = keys + (long)kExtSlotWords * (kExtSlots * q + j);
-#pragma unroll
-                for (int v = 0; v < kExtVals; ++v) {
-                    const unsigned long long x = kl[v];
-                    k[v] = ext_is_min(v) ? (x < k[v] ? x : k[v]) : (x > k[v] ? x : k[v]);
-                    kl[v] = dkey(ext_is_min(v) ? INFINITY : -INFINITY);
-                }
-            }
-            for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-                for (int v = 0; v < kExtVals; ++v) {
-                    const unsigned long long x = __shfl_xor(k[v], o, 64);
-                    k[v] = ext_is_min(v) ? (x < k[v] ? x : k[v]) : (x > k[v] ? x : k[v]);
-                }
-            if (l == 0) {
-                double* e = send + 4 * rs + 8 * q;
-#pragma unroll
-                for (int v = 0; v < kExtVals; ++v) e[v] = dkey_inv(k[v]);
-            }
-        }
-    }
-}
-
-__global__ void k_ext_reset(unsigned long long* __restrict__ keys, int nsub) {
-    for (int i = threadIdx.x; i < kExtSlots * nsub; i += blockDim.x) {
-        unsigned long long* kl = keys + (long)kExtSlotWords * i;
-#pragma unroll
-        for (int v = 0; v < kExtVals; ++v) kl[v] = dkey(ext_is_min(v) ? INFINITY : -INFINITY);
-    }
-}
-
-// Guard of one sub-step: every agent outside rank's candidate rows is farther than the cull
-// radius (in y) from every agent rank computed.  Record layout (per rank q, per sub-step): {min y,
-// max y of q's computed rows, max y of q's owned rows below its top `guard` rows, min y above its
-// bottom `guard` rows, min y, max y of q's owned rows}.
-__device__ __forceinline__ bool halo_guard_ok(const double* E, long stride, int ws, int rank, double radius) {
-    const double rm = radius * (1.0 + 1e-9) + 1e-12;
-    const double* me = E + (long)rank * stride;
-    const double ymin = me[0], ymax = me[1];
-    if (!(ymin <= ymax)) return true;  // no computed agents recorded (identity record)
-    bool ok = true;
-    for (int q = 0; q < ws; ++q) {
-        const double* o = E + (long)q * stride;
-        if (q < rank) {  // rows below: rank-1's rows outside our candidate band, all of lower ranks
-            const double lim = (q == rank - 1) ? o[2] : o[5];
-            if (!(ymin - lim > rm)) ok = false;
-        } else if (q > rank) {
-            const double lim = (q == rank + 1) ? o[3] : o[4];
-            if (!(lim - ymax > rm)) ok = false;
-        }
-    }
-    return ok;
-}
-
-// Window halo rows from the gathered slabs (rank-1's last rows below, rank+1's first rows above);
-// block 0 lane 0 runs the guard on the gathered extents.
-__global__ void __launch_bounds__(kBlock) k_halo_unpack(int W, int halo, int rows_lo, int rows_hi, long hi_off,
-                                                        const double* __restrict__ recv, long stride, int ws, int rank,
-                                                        double radius, int nsub, double2* __restrict__ wpos,
-                                                        int32_t* __restrict__ flag) {
-    const long t = (long)blockIdx.x * kBlock + threadIdx.x;
-    const long nlo = (long)rows_lo * W, nhi = (long)rows_hi * W, rs = (long)halo * W;
-    if (t < nlo) {
-        const double2* src = reinterpret_cast<const double2*>(recv + (long)(rank - 1) * stride) + rs + (rs - nlo);
-        wpos[t] = src[t];
-    } else if (t < nlo + nhi) {
-        const double2* src = reinterpret_cast<const double2*>(recv + (long)(rank + 1) * stride);
-        wpos[hi_off + (t - nlo)] = src[t - nlo];
-    }
-    if (blockIdx.x == 0 && threadIdx.x < nsub && !halo_guard_ok(recv + 4 * rs + 8 * threadIdx.x, stride, ws, rank, radius))
-        atomicOr(flag, 1);
-}
-
-// ---- neighbour exchange (one all_to_all_single): rank r sends its first G rows to r-1 and its
-// last G rows to r+1 only, and its nsub guard records (8 doubles each) to every rank, which the
-// guard needs from all of them.  Chunk q of the send buffer (to rank q) and of the receive buffer
-// (from rank q) are [records (8 nsub) | rows (G W double2s) if q = r +- 1]: the two layouts have the
-// same sizes, so one offset formula serves both (cbf_amd/shard.py: ShardedLattice.nbr_splits).
-__device__ __forceinline__ long nbr_chunk_off(int q, int rank, int ws, long r8, long rs2) {
-    long o = (long)q * r8;
-    if (rank > 0 && q > rank - 1) o += rs2;
-    if (rank + 1 < ws && q > rank + 1) o += rs2;
-    return o;
-}
-
-// rows: thread t < n_lo copies the first G rows (to rank - 1), the next n_hi the last G rows (to
-// rank + 1); block 0 reduces the guard records as k_halo_pack does and writes them into every chunk
-__global__ void __launch_bounds__(kBlock) k_halo_pack_nbr(int W, int halo, long n_own, const double2* __restrict__ own,
-                                                          unsigned long long* __restrict__ keys, int nsub, int ws,
-                                                          int rank, double* __restrict__ send) {
-    const long t = (long)blockIdx.x * kBlock + threadIdx.x;
-    const long rs = (long)halo * W, r8 = 8l * nsub;
-    const long n_lo = rank > 0 ? rs : 0, n_hi = rank + 1 < ws ? rs : 0;
-    if (t < n_lo) {
-        reinterpret_cast<double2*>(send + nbr_chunk_off(rank - 1, rank, ws, r8, 2 * rs) + r8)[t] = own[t];
-    } else if (t < n_lo + n_hi) {
-        const long i = t - n_lo;
-        reinterpret_cast<double2*>(send + nbr_chunk_off(rank + 1, rank, ws, r8, 2 * rs) + r8)[i] = own[n_own - rs + i];
-    }
-    if (blockIdx.x == 0) {
-        const int l = threadIdx.x & 63;
-        for (int q = threadIdx.x >> 6; q < nsub; q += kBlock / 64) {
-            unsigned long long k[kExtVals];
-#pragma unroll
-            for (int v = 0; v < kExtVals; ++v) k[v] = dkey(ext_is_min(v) ? INFINITY : -INFINITY);
-            for (int j = l; j < kExtSlots; j += 64) {
-                unsigned long long* kl = keys + (long)kExtSlotWords * (kExtSlots * q + j);
-#pragma unroll
-                for (int v = 0; v < kExtVals; ++v) {
-                    const unsigned long long x = kl[v];
-                    k[v] = ext_is_min(v) ? (x < k[v] ? x : k[v]) : (x > k[v] ? x : k[v]);
-                    kl[v] = dkey(ext_is_min(v) ? INFINITY : -INFINITY);
-                }
-            }
-            for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-                for (int v = 0; v < kExtVals; ++v) {
-                    const unsigned long long x = __shfl_xor(k[v], o, 64);
-                    k[v] = ext_is_min(v) ? (x < k[v] ? x : k[v]) : (x > k[v] ? x : k[v]);
-                }
-            // lane d writes the record into the chunks of destinations d, d + 64, ...
-            for (int d = l; d < ws; d += 64) {
-                double* e = send + nbr_chunk_off(d, rank, ws, r8, 2 * rs) + 8 * q;
-#pragma unroll
-                for (int v = 0; v < kExtVals; ++v) e[v] = dkey_inv(k[v]);
-            }
-        }
-    }
-}
-
-// the guard of one sub-step over records at recv + off(q) + 8 s (halo_guard_ok's rule)
-__device__ __forceinline__ bool halo_guard_ok_nbr(const double* recv, int s, int ws, int rank, long r8, long rs2,
-                                                  double radius) {
-    const double rm = radius * (1.0 + 1e-9) + 1e-12;
-    const double* me = recv + nbr_chunk_off(rank, rank, ws, r8, rs2) + 8 * s;
-    const double ymin = me[0], ymax = me[1];
-    if (!(ymin <= ymax)) return true;
-    bool ok = true;
-    for (int q = 0; q < ws; ++q) {
-        const double* o = recv + nbr_chunk_off(q, rank, ws, r8, rs2) + 8 * s;
-        if (q < rank) {
-            const double lim = (q == rank - 1) ? o[2] : o[5];
-            if (!(ymin - lim > rm)) ok = false;
-        } else if (q > rank) {
-            const double lim = (q == rank + 1) ? o[3] : o[4];
-            if (!(lim - ymax > rm)) ok = false;
-        }
-    }
-    return ok;
-}
-
-// Window ghost rows from the neighbours' chunks (rank-1's last rows_lo rows below, rank+1's first
-// rows_hi rows above); block 0 lanes s < nsub run the guard of sub-step s.
-__global__ void __launch_bounds__(kBlock) k_halo_unpack_nbr(int W, int halo, int rows_lo, int rows_hi, long hi_off,
-                                                            const double* __restrict__ recv, int ws, int rank,
-                                                            double radius, int nsub, double2* __restrict__ wpos,
-                                                            int32_t* __restrict__ flag) {
-    const long t = (long)blockIdx.x * kBlock + threadIdx.x;
-    const long nlo = (long)rows_lo * W, nhi = (long)rows_hi * W, rs = (long)halo * W, r8 = 8l * nsub;
-    if (t < nlo) {
-        const double2* src = reinterpret_cast<const double2*>(recv + nbr_chunk_off(rank - 1, rank, ws, r8, 2 * rs) + r8);
-        wpos[t] = src[rs - nlo + t];
-    } else if (t < nlo + nhi) {
-        const double2* src = reinterpret_cast<const double2*>(recv + nbr_chunk_off(rank + 1, rank, ws, r8, 2 * rs) + r8);
-        wpos[hi_off + (t - nlo)] = src[t - nlo];
-    }
-    if (blockIdx.x == 0 && threadIdx.x < nsub && !halo_guard_ok_nbr(recv, threadIdx.x, ws, rank, r8, 2 * rs, radius))
-        atomicOr(flag, 1);
-}
-
-}  // namespace
-
-extern "C" int64_t cbf_halo_nbr_elems(int32_t W, int32_t halo, int32_t nsub, int32_t world_size, int32_t rank) {
-    if (W <= 0 || halo <= 0 || nsub < 1 || world_size < 1 || rank < 0 || rank >= world_size) return -1;
-    const long r8 = 8l * nsub, rs2 = 2l * halo * W;
-    return (int64_t)(world_size * r8 + (rank > 0 ? rs2 : 0) + (rank + 1 < world_size ? rs2 : 0));
-}
-
-extern "C" int cbf_halo_pack_nbr(int32_t W, int32_t halo, int64_t n_own, const double* own, uint64_t* ext_keys,
-                                 int32_t nsub, int32_t world_size, int32_t rank, double* send, void* stream) {
-    if (W <= 0 || halo <= 0 || n_own < 2l * halo * W || !own || !ext_keys || !send || nsub < 1 || nsub > 64 ||
-        world_size < 1 || rank < 0 || rank >= world_size)
-        return CBF_EINVAL;
-    const long rs = (long)halo * W;
-    const long n = (rank > 0 ? rs : 0) + (rank + 1 < world_size ? rs : 0);
-    hipLaunchKernelGGL(k_halo_pack_nbr, dim3(nblk(n > 0 ? n : 1)), dim3(kBlock), 0, (hipStream_t)stream, W, halo,
-                       (long)n_own, reinterpret_cast<const double2*>(own),
-                       reinterpret_cast<unsigned long long*>(ext_keys), nsub, world_size, rank, send);
-    return (int)hipGetLastError();
-}
-
-extern "C" int cbf_halo_unpack_nbr(int32_t W, int32_t halo, int32_t rows_lo, int32_t rows_hi, int64_t hi_row_offset,
-                                   const double* recv, int32_t world_size, int32_t rank, double radius, int32_t nsub,
-                                   double* wpos, int32_t* flag, void* stream) {
-    if (W <= 0 || halo <= 0 || rows_lo < 0 || rows_hi < 0 || rows_lo > halo || rows_hi > halo || !recv || !wpos ||
-        !flag || world_size < 1 || rank < 0 || rank >= world_size || nsub < 1 || nsub > 64 ||
-        (rows_lo > 0 && rank == 0) || (rows_hi > 0 && rank == world_size - 1) || hi_row_offset < 0)
-        return CBF_EINVAL;
-    const long n = (long)(rows_lo + rows_hi) * W;
-    hipLaunchKernelGGL(k_halo_unpack_nbr, dim3(nblk(n > 0 ? n : 1)), dim3(kBlock), 0, (hipStream_t)stream, W, halo,
-                       rows_lo, rows_hi, (long)hi_row_offset * W, recv, world_size, rank, radius, nsub,
-                       reinterpret_cast<double2*>(wpos), flag);
-    return (int)hipGetLastError();
-}
-
-extern "C" size_t cbf_halo_ext_bytes(int32_t nsub) {
-    return nsub < 1 ? 0 : (size_t)nsub * kExtSlots * kExtSlotWords * sizeof(unsigned long long);
-}
-
-extern "C" int cbf_halo_ext_reset(uint64_t* ext_keys, int32_t nsub, void* stream) {
-    if (!ext_keys || nsub < 1) return CBF_EINVAL;
-    hipLaunchKernelGGL(k_ext_reset, dim3(1), dim3(kBlock), 0, (hipStream_t)stream,
-                       reinterpret_cast<unsigned long long*>(ext_keys), nsub);
-    return (int)hipGetLastError();
-}
-
-extern "C" int cbf_halo_pack(int32_t W, int32_t halo, int64_t n_own, const double* own, uint64_t* ext_keys,
-                             int32_t nsub, double* send, void* stream) {
-    if (W <= 0 || halo <= 0 || n_own < 2l * halo * W || !own || !ext_keys || !send || nsub < 1) return CBF_EINVAL;
-    const long n = 2l * halo * W;
-    hipLaunchKernelGGL(k_halo_pack, dim3(nblk(n)), dim3(kBlock), 0, (hipStream_t)stream, W, halo, (long)n_own,
-                       reinterpret_cast<const double2*>(own), reinterpret_cast<unsigned long long*>(ext_keys), nsub,
-                       send);
-    return (int)hipGetLastError();
-}
-
-extern "C" int cbf_halo_unpack(int32_t W, int32_t halo, int32_t rows_lo, int32_t rows_hi, int64_t hi_row_offset,
-                               const double* recv, int64_t stride, int32_t world_size, int32_t rank, double radius,
-                               int32_t nsub, double* wpos, int32_t* flag, void* stream) {
-    if (W <= 0 || halo <= 0 || rows_lo < 0 || rows_hi < 0 || rows_lo > halo || rows_hi > halo || !recv || !wpos ||
-        !flag || world_size < 1 || rank < 0 || rank >= world_size || nsub < 1 || nsub > 64 ||
-        stride < 4l * halo * W + 8l * nsub || (rows_lo > 0 && rank == 0) || (rows_hi > 0 && rank == world_size - 1) ||
-        hi_row_offset < 0)
-        return CBF_EINVAL;
-    const long n = (long)(rows_lo + rows_hi) * W;
-    hipLaunchKernelGGL(k_halo_unpack, dim3(nblk(n > 0 ? n : 1)), dim3(kBlock), 0, (hipStream_t)stream, W, halo,
-                       rows_lo, rows_hi, (long)hi_row_offset * W, recv, (long)stride, world_size, rank, radius, nsub,
-                       reinterpret_cast<double2*>(wpos), flag);
-    return (int)hipGetLastError();
 }

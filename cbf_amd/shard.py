@@ -183,39 +183,34 @@ class HipBackend:
             L.stream_handle()), "cbf_lattice_cycle_sharded_ex")
         self._checked(f"cbf_lattice_cycle_sharded (sub-steps {s0}..{s1 - 1}, stats {S.collect_stats})", S)
 
+    def _last_sub_args(self, S):
+        """Leading arguments of a build / advance of a cycle's last sub-step: parameters, grid, owned
+        rows, the sub-step's window and its positions within the cycle window."""
+        L, W, sub = self._lib, self.W, S.subs[-1]
+        return (self.cp, L.C.byref(self.grid), W, self.H, S.rb, S.re, sub.w0, sub.w1 - sub.w0,
+                L.ptr(S.wpos[(sub.w0 - S.w0) * W:]))
+
     def lattice_build(self, S):
         L, P = self._lib, self._lib.ptr
-        sub = S.subs[-1]
-        if self.cull == "window":
-            L.check(L.lib.cbf_lattice_window_build_ex(
-                self.cp, L.C.byref(self.grid), self.W, self.H, S.rb, S.re, sub.w0, sub.w1 - sub.w0,
-                P(S.wpos[(sub.w0 - S.w0) * self.W:]), self.gain, P(S.vel), P(self.wss[-1]), self.ws_bytes,
-                L.stream_handle()), "cbf_lattice_window_build_ex")
-            return
-        L.check(L.lib.cbf_lattice_build(self.cp, L.C.byref(self.grid), self.W, self.H, S.rb, S.re, sub.w0,
-                                        sub.w1 - sub.w0, P(S.wpos[(sub.w0 - S.w0) * self.W:]), self.gain, P(S.vel),
-                                        P(self.wss[-1]), self.ws_bytes, L.stream_handle()), "cbf_lattice_build")
+        name = "cbf_lattice_window_build_ex" if self.cull == "window" else "cbf_lattice_build"
+        L.check(getattr(L.lib, name)(*self._last_sub_args(S), self.gain, P(S.vel), P(self.wss[-1]), self.ws_bytes,
+                                     L.stream_handle()), name)
 
     def lattice_advance(self, S, mark=None, commit=True):
         L, P = self._lib, self._lib.ptr
-        sub = S.subs[-1]
+        out = (P(S.u), P(S.status), P(S.nbr_count))
+        tail = (P(S.stats_ptr()), P(self.wss[-1]), self.ws_bytes,
+                L.C.c_void_p(mark.cuda_event if mark is not None else 0), L.stream_handle())
         if self.cull == "window":   # new owned positions into scratch (the filter reads the window throughout)
             if getattr(self, "_own_next", None) is None:
                 self._own_next = self.torch.empty_like(S.own)
-            L.check(L.lib.cbf_lattice_window_advance_ex(
-                self.cp, L.C.byref(self.grid), self.W, self.H, S.rb, S.re, sub.w0, sub.w1 - sub.w0,
-                P(S.wpos[(sub.w0 - S.w0) * self.W:]), self.T, P(self._own_next), P(S.u), P(S.status),
-                P(S.nbr_count), P(S.stats_ptr()), P(self.wss[-1]), self.ws_bytes,
-                L.C.c_void_p(mark.cuda_event if mark is not None else 0), L.stream_handle()),
-                "cbf_lattice_window_advance_ex")
+            L.check(L.lib.cbf_lattice_window_advance_ex(*self._last_sub_args(S), self.T, P(self._own_next), *out,
+                                                        *tail), "cbf_lattice_window_advance_ex")
             if commit:
                 S.own.copy_(self._own_next)
             return
-        L.check(L.lib.cbf_lattice_advance_marked(
-            self.cp, L.C.byref(self.grid), self.W, self.H, S.rb, S.re, sub.w0, sub.w1 - sub.w0,
-            P(S.wpos[(sub.w0 - S.w0) * self.W:]), self.T, P(S.own), P(S.u), P(S.status), P(S.nbr_count), sub.guard,
-            None, P(S.stats_ptr()), P(self.wss[-1]), self.ws_bytes,
-            L.C.c_void_p(mark.cuda_event if mark is not None else 0), L.stream_handle()), "cbf_lattice_advance_marked")
+        L.check(L.lib.cbf_lattice_advance_marked(*self._last_sub_args(S), self.T, P(S.own), *out, S.subs[-1].guard,
+                                                 None, *tail), "cbf_lattice_advance_marked")
 
     def arm_guard_readback(self):
         """Queue a copy of the guard flag to pinned host memory behind this exchange's unpack."""
@@ -353,7 +348,7 @@ class ShardedLattice:
         """Chunk sizes (doubles) of the neighbour exchange's send and receive buffers, in rank
         order: every rank gets this rank's 8 nsub doubles of guard records, ranks rank - 1 and
         rank + 1 also its first / last G rows (rows_elems doubles); receiving mirrors it
-        (cbf_halo_nbr_elems, nbr_chunk_off in swarm.hip)."""
+        (cbf_halo_nbr_elems, nbr_chunk_off in halo.hip)."""
         return [8 * nsub + (rows_elems if abs(q - rank) == 1 else 0) for q in range(ws)]
 
     def chunk_offset(self, q):

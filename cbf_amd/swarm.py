@@ -493,52 +493,32 @@ class LatticeSwarm:
         kernel's own start and end times (cbf_lattice_*advance_timed, hipExtLaunchKernel).
         Window cull: the new positions go to a scratch tensor (the filter reads pos throughout) and
         are copied into pos unless commit=False (kernel timing)."""
-        ev = (lambda e: _lib.C.c_void_p(e.cuda_event))
+        ev = (lambda e: _lib.C.c_void_p(e.cuda_event if e is not None else 0))
+        events = (ev(timing[0]), ev(timing[1])) if timing is not None else (ev(mark),)
+        out = (ptr(self.u), ptr(self.status), ptr(self.nbr_count))
+        tail = (self._st(), ptr(self.ws), self.ws_bytes)
         if self.cull == "window":
             torch = _lib.require_gpu()
             if getattr(self, "_pos_next", None) is None:
                 self._pos_next = torch.empty_like(self.pos)
-            if timing is not None:
-                check(lib.cbf_lattice_window_advance_timed(
-                    self.cp, _lib.C.byref(self.grid), self.W, self.H, ptr(self.pos), self.T, ptr(self._pos_next),
-                    ptr(self.u), ptr(self.status), ptr(self.nbr_count), self._st(), ptr(self.ws), self.ws_bytes,
-                    ev(timing[0]), ev(timing[1]), stream_handle()), "cbf_lattice_window_advance_timed")
-                if commit:
-                    self.pos.copy_(self._pos_next)
-                return
-            check(lib.cbf_lattice_window_advance(self.cp, _lib.C.byref(self.grid), self.W, self.H, ptr(self.pos),
-                                                 self.T, ptr(self._pos_next), ptr(self.u), ptr(self.status),
-                                                 ptr(self.nbr_count), self._st(), ptr(self.ws), self.ws_bytes,
-                                                 _lib.C.c_void_p(mark.cuda_event if mark is not None else 0),
-                                                 stream_handle()), "cbf_lattice_window_advance")
+            name = "cbf_lattice_window_advance_timed" if timing is not None else "cbf_lattice_window_advance"
+            check(getattr(lib, name)(self.cp, _lib.C.byref(self.grid), self.W, self.H, ptr(self.pos), self.T,
+                                     ptr(self._pos_next), *out, *tail, *events, stream_handle()), name)
             if commit:
                 self.pos.copy_(self._pos_next)
             return
+        # the whole lattice in place, no guard rows, no extents
+        args = (_lib.C.byref(self.grid), self.W, self.H, 0, self.H, 0, self.H, ptr(self.pos), self.T, ptr(self.pos),
+                *out, 0, None, *tail)
         if self.barrier == "euclidean_hocbf":
-            check(lib.cbf_lattice_advance_hocbf(self.cp, _lib.C.byref(self.hp), _lib.C.byref(self.grid), self.W,
-                                                self.H, 0, self.H, 0, self.H, ptr(self.pos), self.T, ptr(self.pos),
-                                                ptr(self.u), ptr(self.status), ptr(self.nbr_count), 0, None,
-                                                self._st(), ptr(self.ws), self.ws_bytes, stream_handle()),
-                  "cbf_lattice_advance_hocbf")
-            return
-        if timing is not None:
-            check(lib.cbf_lattice_advance_timed(self.cp, _lib.C.byref(self.grid), self.W, self.H, 0, self.H, 0, self.H,
-                                                ptr(self.pos), self.T, ptr(self.pos), ptr(self.u), ptr(self.status),
-                                                ptr(self.nbr_count), 0, None, self._st(), ptr(self.ws), self.ws_bytes,
-                                                ev(timing[0]), ev(timing[1]), stream_handle()),
-                  "cbf_lattice_advance_timed")
-            return
-        if mark is not None:
-            check(lib.cbf_lattice_advance_marked(self.cp, _lib.C.byref(self.grid), self.W, self.H, 0, self.H, 0, self.H,
-                                                 ptr(self.pos), self.T, ptr(self.pos), ptr(self.u), ptr(self.status),
-                                                 ptr(self.nbr_count), 0, None, self._st(), ptr(self.ws), self.ws_bytes,
-                                                 _lib.C.c_void_p(mark.cuda_event), stream_handle()),
-                  "cbf_lattice_advance_marked")
-            return
-        check(lib.cbf_lattice_advance(self.cp, _lib.C.byref(self.grid), self.W, self.H, 0, self.H, 0, self.H,
-                                      ptr(self.pos), self.T, ptr(self.pos), ptr(self.u), ptr(self.status),
-                                      ptr(self.nbr_count), 0, None, self._st(), ptr(self.ws), self.ws_bytes,
-                                      stream_handle()), "cbf_lattice_advance")
+            name, args = "cbf_lattice_advance_hocbf", (_lib.C.byref(self.hp),) + args
+        elif timing is not None:
+            name, args = "cbf_lattice_advance_timed", args + events
+        elif mark is not None:
+            name, args = "cbf_lattice_advance_marked", args + events
+        else:
+            name = "cbf_lattice_advance"
+        check(getattr(lib, name)(self.cp, *args, stream_handle()), name)
 
     def stats_summary(self) -> dict:
         """Rollout statistics since the last reset (host sync); raises if a step's cell list was

@@ -156,7 +156,7 @@ def test_sharded_rollout_equals_single_lattice(ws, k, exchange):
 
 
 def test_neighbour_splits_send_rows_to_neighbours_only():
-    """Chunk sizes of the neighbour exchange (cbf_halo_nbr_elems / nbr_chunk_off in swarm.hip):
+    """Chunk sizes of the neighbour exchange (cbf_halo_nbr_elems / nbr_chunk_off in halo.hip):
     records to every rank, rows only to rank +- 1, and a symmetric send / receive pattern."""
     ws, rows, k = 5, 100, 3
     for r in range(ws):
